@@ -24,6 +24,14 @@ tables, the Gram and the SE statistics are all-reduced over RCCL (clustered scor
 their owner ranks by cluster key); ``--shard rows`` shards contiguous row blocks (every
 group table all-reduced).  Timing: W warm-up steps, barrier + device
 sync, K timed steps, device sync + barrier; the max over ranks is reported.
+
+A plain run does only what the result line's ``value`` / ``ms_per_step`` need: set-up, warm-up,
+the K timed steps, the line.  ``--full`` adds the measurements that take runs of their own: the
+per-kernel pass (``kernels_ms``, ``roofline``), ``cpu_baseline`` and ``h2d`` (each can be switched
+off with ``--no-prof`` / ``--no-cpu`` / ``--no-h2d``); without it those fields are empty.
+``--dump-outputs DIR`` writes what the last timed step returned (``solve_step``: beta, se, rss,
+counts) as ``DIR/<name>.npy`` in float64; the panel depends only on the arguments (``--seed``), so
+two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -86,10 +94,16 @@ def parse(argv=None):
     ap.add_argument("--emulate-rank", type=str, default=None, metavar="R/N",
                     help="diagnostic: solve rank R's owner shard of an N-rank strong-scaled run alone on one "
                          "GPU (no collectives): the per-rank compute and fixed cost of the N-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: per-kernel "
+                         "times and the roofline (a second pass of the steps), the CPU baseline and the "
+                         "host-to-device load")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-rows", type=int, default=50_000_000, help="CPU baseline sample (prefix rows)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="diagnostic: no per-kernel events (no roofline)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-h2d", action="store_true", help="with --full: no host-to-device load")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: no per-kernel events (no roofline)")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE",
                     help="A/B only: an engine test knob (lfe_test_set_knob); the engine reads no environment")
@@ -376,6 +390,24 @@ def cpu_baseline(a, cols, codes) -> dict:
     return out
 
 
+def output_arrays(res: dict) -> dict:
+    """What ``solve_step`` returned, as float64 arrays by name (scalars as 1-element arrays; an
+    entry that is None, e.g. ``n_clusters`` of an unclustered fit, is left out)."""
+    import numpy as np
+
+    return {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in res.items() if v is not None}
+
+
+def dump_outputs(res: dict, path: str) -> None:
+    """``--dump-outputs``: one ``<name>.npy`` per array of ``output_arrays`` (a few hundred bytes
+    in all: the fit's outputs are k-vectors and scalars)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, arr in output_arrays(res).items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main(argv=None):
     a = parse(argv)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -383,8 +415,11 @@ def main(argv=None):
         sys.exit(spawn_ranks(a.gpus, sys.argv[1:] if argv is None else list(argv)))
 
     if a.print_rank_env:
-        print(json.dumps({k: os.environ.get(k) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR")}),
-              flush=True)
+        # one write per line: the ranks share the launcher's stdout, and print() writes the text and
+        # the newline separately, so two ranks' lines could run together
+        sys.stdout.write(json.dumps({k: os.environ.get(k) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE",
+                                                                    "MASTER_ADDR")}) + "\n")
+        sys.stdout.flush()
         return
 
     import numpy as np
@@ -439,10 +474,12 @@ def main(argv=None):
     per_step = sorted(s / m for s, m in zip(run_s, sizes))
     med_step = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (
         per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
-    # per-kernel times from a second pass of the same steps with an event pair around every
+    if a.dump_outputs and d.rank == 0:  # every rank holds the same all-reduced results
+        dump_outputs(res, a.dump_outputs)
+    # --full: per-kernel times from a second pass of the same steps with an event pair around every
     # launch (the events cost ~0.2 ms of host time per step, so they stay out of `value`)
     kstats = {}
-    if not a.no_prof:
+    if a.full and not a.no_prof:
         eng.profile(True)
         for _ in range(a.steps):
             solve_step(eng, a.vcov, n_cl)
@@ -494,7 +531,7 @@ def main(argv=None):
                                           "model": f"{passes} pass(es) over X (8p B/row) + codes (4F B/row)"}
 
     extra = {}
-    if d.rank == 0 and d.world == 1 and (not a.no_cpu or not a.no_h2d):
+    if a.full and d.rank == 0 and d.world == 1 and (not a.no_cpu or not a.no_h2d):
         cols, codes = eng.copy_inputs()
         if not a.no_cpu:
             extra["cpu_baseline"] = cpu_baseline(a, cols, codes)

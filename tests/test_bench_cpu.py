@@ -63,6 +63,32 @@ def test_presets_and_labels():
     assert (a1.rows, a1.k, a1.levels, a1.vcov) == (1_000_000, 3, [20_000, 500], "iid")
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None
+    assert sum(bench.split_runs(a.steps, a.runs)) == 7  # --steps is the number of timed steps
+    assert sum(bench.split_runs(3, 5)) == 3 and sum(bench.split_runs(1, 5)) == 1
+    b = bench.parse(["--full", "--no-cpu", "--dump-outputs", "some/dir"])
+    assert b.full and b.no_cpu and not b.no_h2d and not b.no_prof and b.dump_outputs == "some/dir"
+
+
+def test_dump_outputs_writes_one_float64_array_per_result(tmp_path):
+    import numpy as np
+
+    res = dict(n_obs=99, iterations=7, beta=np.array([1.5, -2.0]), se=np.array([0.1, 0.2], dtype=np.float32),
+               df_resid=90, fe_dims=[5, 3], n_clusters=None, rss=3.25, beta_dev_vs_host=1e-15)
+    out = tmp_path / "a" / "b"  # created on demand
+    bench.dump_outputs(res, str(out))
+    assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in res if k != "n_clusters")
+    for k, v in res.items():
+        if v is not None:
+            arr = np.load(out / (k + ".npy"))
+            assert arr.dtype == np.float64 and arr.ndim == 1
+            np.testing.assert_array_equal(arr, np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    res["n_clusters"] = (40, 50, 1900)
+    assert bench.output_arrays(res)["n_clusters"].tolist() == [40.0, 50.0, 1900.0]
+
+
 def test_step_byte_model_covers_the_headline_kernels():
     ab = bench.algorithmic_bytes(50_000_000, 11, 2)
     for k in ("part_scatter", "group_sums", "gram_resid", "tp", "tq", "layout_scatter", "layout_hist"):

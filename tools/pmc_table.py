@@ -1,4 +1,4 @@
-"""Per-kernel table from tools/pmc.sh output (gpurun_out/pmc/<pass>/run_counter_collection.csv).
+"""Per-kernel table from tools/pmc.sh output ($OUT_DIR/pmc/<pass>/run_counter_collection.csv).
 
 Averages each counter over the dispatches of a kernel (the last `--last` dispatches,
 i.e. the timed steps).  FETCH_SIZE is doubled (gfx950 reports half the bytes of a
@@ -11,7 +11,7 @@ import re
 import sys
 from collections import defaultdict
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.environ.get("OUT_DIR", "bench_out"), "pmc")
 vals = defaultdict(lambda: defaultdict(list))   # kernel -> counter -> [per dispatch]
 dur = defaultdict(list)
 for f in glob.glob(os.path.join(root, "*", "run_counter_collection.csv")):

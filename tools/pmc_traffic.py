@@ -1,6 +1,6 @@
 """HBM traffic per launch of each engine kernel from rocprofv3 PMC passes.
 
-Reads gpurun_out/pmc/{fetch,write}/run_counter_collection.csv (tools/pmc.sh, one
+Reads bench_out/pmc/{fetch,write}/run_counter_collection.csv (tools/pmc.sh, one
 counter per pass, never combined with tracing) and writes a JSON keyed by the
 engine's kernel ids (the names bench.py reports):
 
@@ -9,7 +9,7 @@ engine's kernel ids (the names bench.py reports):
 FETCH_SIZE is doubled per MI355X_MICROARCH.md "HBM": on gfx950 it reports half
 the bytes of a wide streaming read.  Launches of the timed steps are averaged.
 
-    python tools/pmc_traffic.py gpurun_out/pmc profiles/r01/pmc_traffic.json --rows 50000000 --k 10 \
+    python tools/pmc_traffic.py bench_out/pmc profiles/r01/pmc_traffic.json --rows 50000000 --k 10 \
         --levels 100000,1000 --vcov HC1
 """
 import argparse
